@@ -9,9 +9,13 @@ data path (weak scaling).  The Metropolis-resampler rate (BASELINE
 1e5 chains, weights = d=32 MVN densities, 1e3 iterations) is measured after the timed region and
 reported as `mh_steps_per_s`.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N --steps K --warmup W
+
+--dump-outputs DIR writes, after the timed steps, the log-densities the last timed step returned as
+DIR/mvn_logpdf.npy (float64; DIR/mvn_logpdf_rank<r>.npy per rank when there are several).  The inputs are
+seeded, so two builds run with the same arguments can be compared output for output.
 
 Both forms run N ranks.  Started WITHOUT a launcher (`WORLD_SIZE` unset) and with --gpus N > 1, this
 process never touches the GPU: it starts `torch.distributed.run` with N fresh child ranks and exits
@@ -46,6 +50,7 @@ C5_N, C5_D = 4_000_000, 256      # BASELINE configs[4]: d=256 MVN, 4e6 particles
 F64_MFMA_PEAK_TFLOPS = 78.6      # public spec; measured 77.7 (profiles/r01_calibration.txt)
 PF_N = 1_000_000                 # BASELINE configs[2]: particle filter, 1e6 particles
 AUX_TIMEOUT_S = 300              # rank 0 prints the headline line by itself if the legs after it hang this long
+DUMP_BUDGET_BYTES = 64 << 20     # --dump-outputs: all ranks' files together stay below this
 
 
 def make_sigma(d, seed):
@@ -109,6 +114,20 @@ def collect_hbm_traffic(n, d, kernel_substr=("logpdf_nb4", "logpdf_mfma")):
         return None
 
 
+def dump_outputs(directory, name, out, rank, world):
+    """--dump-outputs: the device array `out` as DIR/<name>.npy (DIR/<name>_rank<r>.npy when world > 1).  An array
+    larger than this rank's share of DUMP_BUDGET_BYTES is replaced by a fixed sample of its rows (seed 0, in index
+    order), the same rows in every run."""
+    import numpy as np
+    a = out.cpu().numpy()
+    assert a.dtype in (np.float32, np.float64), a.dtype
+    cap = (DUMP_BUDGET_BYTES // world - 128) // (a.itemsize * max(1, a[0].size))  # (128: the .npy header)
+    if a.shape[0] > cap:
+        a = a[np.sort(np.random.default_rng(0).choice(a.shape[0], cap, replace=False))]
+    os.makedirs(directory, exist_ok=True)
+    np.save(os.path.join(directory, name + ("_rank%d" % rank if world > 1 else "") + ".npy"), a)
+
+
 def cpu_baseline(d, budget_s=12.0):
     """The reference's CPU cost structure on this host's cores: per particle a fresh
     distribution, an LU determinant and an LU inverse of Sigma, then the dense quadratic form
@@ -156,6 +175,8 @@ def spawn_ranks(args):
         cmd.append("--no-pmc")
     if args.no_cpu:
         cmd.append("--no-cpu")
+    if args.dump_outputs:
+        cmd += ["--dump-outputs", os.path.abspath(args.dump_outputs)]
     env = dict(os.environ)
     env.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")
     env.setdefault("OMP_NUM_THREADS", "4")
@@ -174,10 +195,15 @@ def main():
                     help="the clock governor needs ~50 ms of load to settle (profiles/r01_calibration.txt)")
     ap.add_argument("--no-pmc", action="store_true", help="skip the rocprofv3 PMC traffic passes")
     ap.add_argument("--no-cpu", action="store_true", help="skip the CPU baseline leg")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="write what the last timed step computed as DIR/<name>.npy")
     args = ap.parse_args()
 
     if args.gpus < 1:
         sys.stderr.write("bench: --gpus must be >= 1\n")
+        return 2
+    if args.steps < 1:
+        sys.stderr.write("bench: --steps must be >= 1\n")
         return 2
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
         return spawn_ranks(args)  # the parent never touches the GPU; the ranks are fresh child processes
@@ -254,6 +280,8 @@ def main():
     if dist_on:
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
     wall_max = float(t.item())
+    if args.dump_outputs:  # before the legs below, which reuse `out`
+        dump_outputs(args.dump_outputs, "mvn_logpdf", out, rank, world)
 
     # a 2048-row sample of the timed launch's inputs and outputs, for the CPU leg's check below
     idx = torch.arange(0, N_PER_GPU, N_PER_GPU // 2048, device="cuda")[:2048]

@@ -12,8 +12,8 @@ Sources of the expected values
     cannot be built here, so these are "parity unpinned" against the reference binary.
   * `resample_*`, `pf_*`: the oracle under the build's Philox contract (the reference's RNG
     cannot be seeded: src/samplers.cpp:10-11).  They pin the contract against drift.
-  * `pf_y`: the first 10 observation rows of the reference's example data data_raw/y_t.csv
-    (an input data file, read as text here; /root/reference is not needed at test time).
+  * `pf_y`: the first 10 observation rows of the reference's example data data_raw/y_t.csv,
+    stored as tests/golden/pf_y.csv.
 """
 import os
 import sys
@@ -74,10 +74,7 @@ def main():
             out["resample_%s_w" % name] = w
             out["resample_%s_B%d" % (name, B)] = O.metropolis(w, B, seed=20240 + B, step=1)
     # ---- a small filter trajectory ----------------------------------------------------------
-    y_rows = np.array([[0, 0], [-1.94145, -1.57094], [-2.07943, -1.67384], [-2.15117, -1.74655]])
-    ref_csv = "/root/reference/data_raw/y_t.csv"
-    if os.path.exists(ref_csv):
-        y_rows = np.loadtxt(ref_csv, delimiter=",", skiprows=1)[:10]
+    y_rows = np.loadtxt(os.path.join(HERE, "pf_y.csv"), delimiter=",", skiprows=1)
     out["pf_y"] = y_rows
     d, N = 2, 64
     I = np.eye(d)
