@@ -676,10 +676,10 @@ CUSMC_EXPORT int cusmc_dist_create(cusmc_ctx *ctx, int kind, const double *mu, c
     dist->lognorm = -0.5 * ((double)d * std::log(2.0 * pi) + logdet);
   } else {
     // log of (pi nu)^(-n/2) det^(-1/2) Gamma((nu+n)/2) / Gamma(nu/2)   :332-340; lgamma, so no
-    // tgamma overflow at d >~ 340; nu + n in float as the reference computes it
+    // tgamma overflow at d >~ 340, and their difference taken without cancellation at large nu
+    // (hostla.h mvt_log_const); nu + n in float as the reference computes it
     const float nu_plus_d = nu + (float)d;
-    dist->lognorm = std::lgamma(0.5 * (double)nu_plus_d) - std::lgamma(0.5 * (double)nu) -
-                    0.5 * (double)d * std::log(pi * (double)nu) - 0.5 * logdet;
+    dist->lognorm = cusmc::la::mvt_log_const((double)nu, (double)nu_plus_d, d) - 0.5 * logdet;
   }
   ctx->dists.push_back(dist);
   *out = dist;
@@ -1163,8 +1163,7 @@ int percov_epilogue(int kind, float nu, int d, int flags, Epilogue *ep)
   ep->inv_nu = kind == CUSMC_MVT ? 1.0 / (double)nu : 0.0;
   // the normalising constants of cusmc_dist_create() without their determinant term
   ep->lognorm = kind == CUSMC_MVN ? -0.5 * (double)d * std::log(2.0 * pi)
-                                  : std::lgamma(0.5 * (double)nu_plus_d) - std::lgamma(0.5 * (double)nu) -
-                                        0.5 * (double)d * std::log(pi * (double)nu);
+                                  : cusmc::la::mvt_log_const((double)nu, (double)nu_plus_d, d);
   return CUSMC_OK;
 }
 

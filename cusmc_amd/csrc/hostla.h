@@ -35,6 +35,28 @@ inline int cholesky(const double *S, int n, std::vector<double> &L)
   return 0;
 }
 
+// log of Gamma((nu + d) / 2) / (Gamma(nu / 2) (pi nu)^(d/2)), nu_plus_d as the caller rounded it (float32 in this
+// library): the Student-t normalising constant without its determinant term.  Evaluated as written, lgamma((nu+d)/2)
+// - lgamma(nu/2) loses the two lgamma values' magnitude in digits -- at nu = 3e7 both are ~2.4e8 and the constant is
+// right to ~1e-8, a float32 error -- and what is left nearly cancels against (d/2) log(pi nu).  From nu = 32 up, with
+// a = nu/2, b = (nu+d)/2, delta = b - a, Stirling's series gives
+//     (a - 1/2) log1p(delta/a) - delta + S(b) - S(a) + delta log(b / (pi nu)) + (delta - d/2) log(pi nu)
+// (S(x) = sum_k B_2k / (2k (2k-1) x^(2k-1)) to k = 8, truncation < 1e-21 at x >= 16; delta - d/2 is exact: the
+// rounding of nu + d), whose terms are all of the size of the result.  Below, the lgamma values are < 28.
+inline double mvt_log_const(double nu, double nu_plus_d, int d)
+{
+  const double pi = 3.14159265358979323846, a = 0.5 * nu, b = 0.5 * nu_plus_d;
+  if (a < 16.0) return std::lgamma(b) - std::lgamma(a) - 0.5 * (double)d * std::log(pi * nu);
+  const double delta = b - a;
+  auto S = [](double x) {
+    const double r = 1.0 / (x * x);
+    return (1.0 / 12.0 + r * (-1.0 / 360.0 + r * (1.0 / 1260.0 + r * (-1.0 / 1680.0 + r * (1.0 / 1188.0 +
+           r * (-691.0 / 360360.0 + r * (1.0 / 156.0 + r * (-3617.0 / 122400.0)))))))) / x;
+  };
+  return (a - 0.5) * std::log1p(delta / a) - delta + (S(b) - S(a)) + delta * std::log(b / (pi * nu)) +
+         (delta - 0.5 * (double)d) * std::log(pi * nu);
+}
+
 // W = L^-1 for lower-triangular L (forward substitution, column by column).
 inline void lower_inverse(const std::vector<double> &L, int n, std::vector<double> &W)
 {
