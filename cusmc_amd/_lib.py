@@ -46,6 +46,11 @@ SYMBOLS = [
     ("cusmc_metropolis_log_dev", _i, [_vp, _vp, _u32, _u32, _u64, _u32, _u32, _u32, _vp]),
     ("cusmc_metropolis_log_host", _i, [_vp, _vp, _u32, _u32, _u64, _u32, _vp]),
     ("cusmc_metropolis_multi_host", _i, [C.POINTER(_i), _i, _vp, _u32, _u32, _u64, _u32, _i, _vp]),
+    ("cusmc_stratified_dev", _i, [_vp, _vp, _u32, _u64, _u32, _u32, _u32, _vp]),
+    ("cusmc_stratified_host", _i, [_vp, _vp, _u32, _u64, _u32, _vp]),
+    ("cusmc_stratified_log_dev", _i, [_vp, _vp, _u32, _u64, _u32, _u32, _u32, _vp]),
+    ("cusmc_stratified_log_host", _i, [_vp, _vp, _u32, _u64, _u32, _vp]),
+    ("cusmc_stratified_multi_host", _i, [C.POINTER(_i), _i, _vp, _u32, _u64, _u32, _i, _vp]),
     ("cusmc_propagate_dev", _i, [_vp, _i, _f, _vp, _vp, _u32, _i, _vp, _vp, _d, _u64, _u32, _u32,
                                  _u32, _vp]),
     ("cusmc_initialize_dev", _i, [_vp, _i, _f, _vp, _vp, _i, _d, _u64, _u32, _u32, _vp]),

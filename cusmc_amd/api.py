@@ -438,6 +438,56 @@ class Sampler:
                                               C.c_void_p(a.data_ptr())))
         return a
 
+    @staticmethod
+    def _stratified(w, N, t, seed, ctx, devices, log_weights):
+        w = _f64(w).reshape(-1)
+        N = w.shape[0] if N is None else int(N)
+        if N > w.shape[0]:
+            raise ValueError("N = %d exceeds the %d weights given" % (N, w.shape[0]))
+        if seed is None:
+            seed = _next_key()
+        a = np.empty(N, dtype=np.uint32)
+        if devices is not None:
+            devs = (C.c_int * len(devices))(*[int(v) for v in devices])
+            check(_lib.lib().cusmc_stratified_multi_host(devs, len(devices), _ptr(w), N, int(seed), int(t),
+                                                         1 if log_weights else 0, _ptr(a)))
+            return a
+        ctx = ctx or default_context()
+        entry = _lib.lib().cusmc_stratified_log_host if log_weights else _lib.lib().cusmc_stratified_host
+        check(entry(ctx._h, _ptr(w), N, int(seed), int(t), _ptr(a)))
+        return a
+
+    @staticmethod
+    def stratified(w, N=None, t=1, seed=None, ctx=None, devices=None):
+        """Stratified resampling of the weight vector w (include/cusmc_hip.h): one
+        Philox-keyed uniform per output in each stratum [i/N, (i+1)/N), cost fixed in N, unbiased for any
+        weights.  Returns the N ancestors (uint32, 0-based, non-decreasing).  devices = [0, 1, ...]: outputs
+        sharded over those GPUs (cusmc_stratified_multi_host), bit-identical to one device."""
+        return Sampler._stratified(w, N, t, seed, ctx, devices, False)
+
+    @staticmethod
+    def stratified_log(logw, N=None, t=1, seed=None, ctx=None, devices=None):
+        """Stratified resampling over LOG-weights (-inf and NaN entries are zero weights): the form for
+        log-densities, which do not underflow at large d."""
+        return Sampler._stratified(logw, N, t, seed, ctx, devices, True)
+
+    @staticmethod
+    def stratified_dev(w, a, t=1, seed=0, first=0, log=False, ctx=None):
+        """Device-resident: w float64 CUDA tensor (all N weights, or log-weights with log=True), a
+        int32/uint32-sized CUDA tensor receiving the ancestors of outputs [first, first + len(a))."""
+        import torch
+        ctx = ctx or default_context()
+        _dev_vector(w, "w", (torch.float64,))
+        _dev_vector(a, "a", _index_dtypes())
+        entry = _lib.lib().cusmc_stratified_log_dev if log else _lib.lib().cusmc_stratified_dev
+        check(entry(ctx._h, C.c_void_p(w.data_ptr()), w.numel(), int(seed), int(t), int(first), a.numel(),
+                    C.c_void_p(a.data_ptr())))
+        return a
+
+    @staticmethod
+    def stratified_log_dev(logw, a, t=1, seed=0, first=0, ctx=None):
+        return Sampler.stratified_dev(logw, a, t=t, seed=seed, first=first, log=True, ctx=ctx)
+
 
 def propagate_dev(X_prev, a, G, Q, X_out, kind="mvn", nu=0.0, scale=1.0, seed=0, step=1, first=0, ctx=None):
     """propagate_K on device-resident tensors (src/mcmc.cpp:90-160):
@@ -596,7 +646,8 @@ def run(N, d, timeSteps, Y, m0, C0, F, G, V, W, df, resampler, distribution, p=0
     """List run(N, d, timeSteps, Y, m0, C0, F, G, V, W, df, resampler, distribution, p)
     -- src/run.rcpp.cpp:58-126.  Returns {"weights": T x N, "posterior_x": T x N x d}.
     df reaches the filter as df (the reference passes it in the wrong slot: SURVEY.md F8).
-    B = 10 is the reference's hard-coded value (src/mcmc.cpp:291).
+    resampler: "metropolis" (the reference's; B = 10 is its hard-coded chain length, src/mcmc.cpp:291) or
+    "stratified" (Sampler.stratified; B is ignored; one device only).
     devices = [0, 1, ...] shards the particles over those GPUs below the C ABI
     (cusmc_pf_run_multi_host; same numbers as one GPU); the environment variable CUSMC_DEVICES="0,1,..."
     does the same for callers that cannot pass the argument (the R package)."""

@@ -128,6 +128,7 @@ struct cusmc_ctx {
   DevBuf scratch[6];  // host-pointer entry points: X, out, w, a, small matrices
   StagingRing ring;  // pinned staging for small parameter uploads
   DevBuf whi;        // high words of the weight vector (resampler, large N)
+  DevBuf strat;      // stratified resampler: partial maxima, tile prefixes, tile-local prefix sums
   DevBuf nb4_pool;   // tail-pool counters of the assembly log-pdf kernel (kernels/logpdf_nb4_gfx950.s)
   cusmc::Nb4Pool nb4_state;
   DevBuf step_mats;  // [Q | G] of the fused filter step, re-uploaded only when they change
@@ -589,6 +590,7 @@ CUSMC_EXPORT int cusmc_ctx_destroy(cusmc_ctx *ctx)
     for (auto &b : ctx->scratch) b.release();
     ctx->draw_img.release();
     ctx->whi.release();
+    ctx->strat.release();
     ctx->nb4_pool.release();
     ctx->step_mats.release();
     ctx->ring.release();
@@ -943,6 +945,107 @@ CUSMC_EXPORT int cusmc_metropolis_log_host(cusmc_ctx *ctx, const double *logw, u
                                            uint64_t seed, uint32_t step, uint32_t *a)
 {
   return routed_metropolis(ctx, logw, N, B, seed, step, true, a);
+}
+
+// ---- stratified resampler -------------------------------------------------------------------
+
+namespace {
+
+int stratified_dev(cusmc_ctx *ctx, const double *w_dev, bool logw, uint32_t N, uint64_t seed, uint32_t step,
+                   uint32_t first, uint32_t count, uint32_t *a_dev)
+{
+  if (int rc = activate(ctx)) return rc;
+  if (N == 0) return fail(CUSMC_EINVAL, "N = 0: no weights to resample");
+  if ((uint64_t)first + count > N) return fail(CUSMC_EINVAL, "shard [%u, %u) exceeds N = %u", first, first + count, N);
+  if (!w_dev || !a_dev) return fail(CUSMC_EINVAL, "null weight or ancestor pointer");
+  if (count == 0) return CUSMC_OK;
+  if (int rc = ctx->strat.reserve(cusmc::stratified_workspace_bytes(N))) return rc;
+  HIP_TRY(cusmc::launch_stratified(w_dev, logw, N, seed, step, first, count, a_dev, ctx->strat.p, ctx->num_cus,
+                                   ctx->stream));
+  return CUSMC_OK;
+}
+
+// one device: upload w, compute outputs [first, first + count), bring them back
+int host_stratified(cusmc_ctx *ctx, const double *w, uint32_t N, uint64_t seed, uint32_t step, bool logw, uint32_t first,
+                    uint32_t count, uint32_t *a)
+{
+  if (int rc = activate(ctx)) return rc;
+  if (count == 0) return CUSMC_OK;
+  if (int rc = ctx->scratch[2].reserve((size_t)N * 8)) return rc;
+  if (int rc = ctx->scratch[3].reserve((size_t)count * 4)) return rc;
+  HIP_TRY(hipMemcpyAsync(ctx->scratch[2].p, w, (size_t)N * 8, hipMemcpyHostToDevice, ctx->stream));
+  if (int rc = stratified_dev(ctx, (const double *)ctx->scratch[2].p, logw, N, seed, step, first, count,
+                              (uint32_t *)ctx->scratch[3].p))
+    return rc;
+  HIP_TRY(hipMemcpyAsync(a, ctx->scratch[3].p, (size_t)count * 4, hipMemcpyDeviceToHost, ctx->stream));
+  HIP_TRY(hipStreamSynchronize(ctx->stream));
+  return CUSMC_OK;
+}
+
+// Outputs sharded over a device list: every device takes the whole weight vector, computes the whole prefix sum
+// and writes outputs [first_r, first_r + count_r); the targets are keyed by the global output index, so the
+// ancestors are the single-device ones bit for bit.
+int multi_stratified(const int *devices, int ndev, const double *w, uint32_t N, uint64_t seed, uint32_t step, bool logw,
+                     uint32_t *a)
+{
+  if (N == 0) return fail(CUSMC_EINVAL, "N = 0: no weights to resample");
+  if (!w || !a) return fail(CUSMC_EINVAL, "null weight or ancestor pointer");
+  if (int rc = check_devices(devices, ndev)) return rc;
+  const int parts = (int)std::min<uint64_t>((uint64_t)ndev, (uint64_t)N);
+  std::lock_guard<std::mutex> lock(g_pool_mutex);
+  DeviceRestore restore;
+  std::vector<cusmc_ctx *> ctxs(parts, nullptr);
+  for (int r = 0; r < parts; ++r)
+    if (int rc = pool_ctx(r, devices[r], &ctxs[r])) return rc;
+  return run_sharded(parts, [&](int r) {
+    uint64_t first, count;
+    shard_range(N, parts, r, &first, &count);
+    return host_stratified(ctxs[r], w, N, seed, step, logw, (uint32_t)first, (uint32_t)count, a + first);
+  });
+}
+
+int routed_stratified(cusmc_ctx *ctx, const double *w, uint32_t N, uint64_t seed, uint32_t step, bool logw, uint32_t *a)
+{
+  if (int rc = activate(ctx)) return rc;
+  if (N == 0) return fail(CUSMC_EINVAL, "N = 0: no weights to resample");
+  if (!w || !a) return fail(CUSMC_EINVAL, "null weight or ancestor pointer");
+  std::vector<int> devs;
+  if (int rc = env_devices(devs)) return rc;
+  if (!devs.empty() && !(devs.size() == 1 && devs[0] == ctx->device))
+    return multi_stratified(devs.data(), (int)devs.size(), w, N, seed, step, logw, a);
+  return host_stratified(ctx, w, N, seed, step, logw, 0, N, a);
+}
+
+}  // namespace
+
+CUSMC_EXPORT int cusmc_stratified_dev(cusmc_ctx *ctx, const double *w_dev, uint32_t N, uint64_t seed, uint32_t step,
+                                      uint32_t first, uint32_t count, uint32_t *a_dev)
+{
+  return stratified_dev(ctx, w_dev, false, N, seed, step, first, count, a_dev);
+}
+
+CUSMC_EXPORT int cusmc_stratified_log_dev(cusmc_ctx *ctx, const double *logw_dev, uint32_t N, uint64_t seed,
+                                          uint32_t step, uint32_t first, uint32_t count, uint32_t *a_dev)
+{
+  return stratified_dev(ctx, logw_dev, true, N, seed, step, first, count, a_dev);
+}
+
+CUSMC_EXPORT int cusmc_stratified_host(cusmc_ctx *ctx, const double *w, uint32_t N, uint64_t seed, uint32_t step,
+                                       uint32_t *a)
+{
+  return routed_stratified(ctx, w, N, seed, step, false, a);
+}
+
+CUSMC_EXPORT int cusmc_stratified_log_host(cusmc_ctx *ctx, const double *logw, uint32_t N, uint64_t seed,
+                                           uint32_t step, uint32_t *a)
+{
+  return routed_stratified(ctx, logw, N, seed, step, true, a);
+}
+
+CUSMC_EXPORT int cusmc_stratified_multi_host(const int *devices, int ndev, const double *w, uint32_t N, uint64_t seed,
+                                             uint32_t step, int log_weights, uint32_t *a)
+{
+  return multi_stratified(devices, ndev, w, N, seed, step, log_weights != 0, a);
 }
 
 // ---- proposal draws -------------------------------------------------------------------------
@@ -1458,8 +1561,11 @@ int pf_run_single(cusmc_ctx *ctx, const double *Y, uint32_t N, int d, uint32_t T
   if (int rc = activate(ctx)) return rc;
   // validate the option strings BEFORE any work: the reference default-constructs an empty
   // std::function for an unknown key and throws bad_function_call mid-run (mcmc.cpp:269-272)
-  if (!resampler || strcmp(resampler, "metropolis") != 0)
-    return fail(CUSMC_EINVAL, "unknown resampler '%s' (known: metropolis)", resampler ? resampler : "(null)");
+  bool stratified;
+  if (resampler && !strcmp(resampler, "metropolis")) stratified = false;
+  else if (resampler && !strcmp(resampler, "stratified")) stratified = true;
+  else
+    return fail(CUSMC_EINVAL, "unknown resampler '%s' (known: metropolis, stratified)", resampler ? resampler : "(null)");
   int kind;
   if (distribution && !strcmp(distribution, "mvn")) kind = CUSMC_MVN;
   else if (distribution && !strcmp(distribution, "mvt")) kind = CUSMC_MVT;
@@ -1537,7 +1643,8 @@ int pf_run_single(cusmc_ctx *ctx, const double *Y, uint32_t N, int d, uint32_t T
   if (rc) return cleanup(rc);
   // MCMC(): for t = 1..T-1: resample -> propagate -> reweight   src/mcmc.cpp:292-308
   if (T > 1) {
-    const bool fused = pf_step_is_fused(d, N);
+    // (the fused step kernel carries the Metropolis chain: the stratified resampler takes the unfused path)
+    const bool fused = !stratified && pf_step_is_fused(d, N);
     rc = pf_obs_table(obs, fused, G, Qw.data(), Y, T, F, ytab);
     if (rc) return cleanup(rc);
     // The fused step carries the resampler's truncated weight table along: the kernel that computes w_t stores its
@@ -1575,7 +1682,8 @@ int pf_run_single(cusmc_ctx *ctx, const double *Y, uint32_t N, int d, uint32_t T
         rc = pf_step_launch(obs, kind, df, w_prev, X_prev, N, B, scale, seed, t, 0, N, a_t, X_t, w_t,
                             CUSMC_OUT_DENSITY, shift_t, bias_t);
       } else {
-        rc = cusmc_metropolis_dev(ctx, w_prev, N, B, seed, t, 0, N, a_t);
+        rc = stratified ? cusmc_stratified_dev(ctx, w_prev, N, seed, t, 0, N, a_t)
+                        : cusmc_metropolis_dev(ctx, w_prev, N, B, seed, t, 0, N, a_t);
         if (!rc) rc = draws(ctx, kind, df, X_prev, a_t, G, Qw.data(), nullptr, d, scale, seed, t, 2u, 0, N, X_t);
         if (!rc) rc = run_logpdf(obs, X_t, N, d, CUSMC_OUT_DENSITY, w_t, shift_t, bias_t);
       }
@@ -1747,8 +1855,11 @@ CUSMC_EXPORT int cusmc_pf_run_multi_host(const int *devices, int ndev, const dou
                                          double scale, uint64_t seed, double *X_out, double *w_out,
                                          uint32_t *a_out)
 {
+  if (resampler && !strcmp(resampler, "stratified"))
+    return fail(CUSMC_EINVAL, "resampler 'stratified' is not available in the sharded filter (its step is the fused "
+                "Metropolis one); run it on one device");
   if (!resampler || strcmp(resampler, "metropolis") != 0)
-    return fail(CUSMC_EINVAL, "unknown resampler '%s' (known: metropolis)", resampler ? resampler : "(null)");
+    return fail(CUSMC_EINVAL, "unknown resampler '%s' (known: metropolis, stratified)", resampler ? resampler : "(null)");
   int kind;
   if (distribution && !strcmp(distribution, "mvn")) kind = CUSMC_MVN;
   else if (distribution && !strcmp(distribution, "mvt")) kind = CUSMC_MVT;

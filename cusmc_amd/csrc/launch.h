@@ -115,6 +115,14 @@ hipError_t launch_metropolis(const double *w, const uint32_t *whi, uint32_t N, u
                              uint32_t step, uint32_t first, uint32_t count, uint32_t *a, int num_cus,
                              hipStream_t stream);
 
+// --- kernels/resample_stratified.hip ------------------------------------------------------------
+// stratified ancestors of outputs [first, first + count) over all N (log-)weights; workspace: device memory of
+// stratified_workspace_bytes(N) (no initialisation needed)
+size_t stratified_workspace_bytes(uint32_t N);
+hipError_t launch_stratified(const double *w, bool log_weights, uint32_t N, uint64_t seed, uint32_t step,
+                             uint32_t first, uint32_t count, uint32_t *a, void *workspace, int num_cus,
+                             hipStream_t stream);
+
 // --- kernels/propagate.hip -----------------------------------------------------------------------
 // X_out[i-first] = [diag(c)] Q (scale xi) + (G ? G X_prev[a ? a[i-first] : i] : m0)
 hipError_t launch_propagate(int kind, float nu, const double *X_prev, const uint32_t *a,

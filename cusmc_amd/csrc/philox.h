@@ -17,6 +17,7 @@
 //             5 chi-square accept / boost uniforms
 //             6 chi-square closed form (integer nu <= 16): uniforms, sub = pair + (block << 16)
 //             8 chi-square closed form, odd nu: the pair's two normals, sub = pair
+//             9 stratified resampler: U_i from words 0, 1 of block (output i, 0, step, 9)
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>

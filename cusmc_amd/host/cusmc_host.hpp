@@ -7,6 +7,7 @@
 //   StatisticalDistribution / MultiVariateNormalDistribution / MultiVariateTStudentDistribution
 //       inst/include/statistics.hpp:36-250   (pdf(y), pdf(y,F), getNorm(), sample(draws,Q,n))
 //   Sampler::metropolis_hastings              inst/include/samplers.hpp:7-18, src/samplers.cpp:7-36
+//   Sampler::stratified                       (no reference counterpart: DESIGN.md section 4.7)
 //   particle_filter                           inst/include/particle_filter.hpp:12-19
 // Errors: the reference dies through Rcpp::stop (inst/include/support.cuh:9-14); here every
 // non-zero ABI status throws cusmc::Error carrying cusmc_last_error().
@@ -170,6 +171,13 @@ class Sampler {
   {
     check(cusmc_metropolis_host(Context::instance().get(), w_t[t - 1].data(), (uint32_t)N, (uint32_t)B, seed,
                                 (uint32_t)t, a_t + (size_t)t * N));
+  }
+  // stratified(a_t, w_t, N, t): the same slots, filled by the stratified resampler (cusmc_stratified_host) -- cost
+  // fixed in N, unbiased for any weights; no chain length
+  static void stratified(unsigned *a_t, const Vector *w_t, size_t N, int t, uint64_t seed = 0)
+  {
+    check(cusmc_stratified_host(Context::instance().get(), w_t[t - 1].data(), (uint32_t)N, seed, (uint32_t)t,
+                                a_t + (size_t)t * N));
   }
 };
 

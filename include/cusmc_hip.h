@@ -175,6 +175,34 @@ int cusmc_metropolis_log_host(cusmc_ctx *ctx, const double *logw, uint32_t N, ui
 int cusmc_metropolis_multi_host(const int *devices, int ndev, const double *w, uint32_t N, uint32_t B,
                                 uint64_t seed, uint32_t step, int log_weights, uint32_t *a);
 
+/* ---- stratified resampler -----------------------------------------------------
+ * Cost fixed in N (four streaming passes), unbiased for every weight vector -- unlike the chain above, whose
+ * bias shrinks only as B grows past max(w) / mean(w).  The reference's Resamplers map (src/mcmc.cpp:252-266) has
+ * no second entry; this one is the lower boundary's extension.  For each i in [first, first+count):
+ *     w_max = largest non-NaN w_j; degenerate (none, w_max <= 0 or +inf): a[i-first] = i.  Otherwise
+ *     q_j = floor(r_j 2^(63 - ceil(log2 N))), r_j = w_j / w_max for w_j > 0 and 0 else; C = inclusive prefix sum of q
+ *     (integers), S = C_{N-1};  U_i = 53-bit uniform of Philox block (i, 0, step, 9);
+ *     x_i = (i + U_i) / N;  T_i = (uint64)(x_i S);  a[i-first] = smallest j with C_j > min(T_i, S - 1).
+ * Zero, negative and NaN weights are never chosen, and a[] is non-decreasing.  Quantising moves less than
+ * N / S < rho / (2^k - rho) ~ rho 2^-k of probability mass in total (total variation; k = 63 - ceil(log2 N),
+ * rho = max(w) / mean(w) <= N).  Keyed by the global index i: shards compose.  N = 0, a shard past N and NULL
+ * pointers are CUSMC_EINVAL. */
+int cusmc_stratified_dev(cusmc_ctx *ctx, const double *w_dev, uint32_t N, uint64_t seed, uint32_t step,
+                         uint32_t first, uint32_t count, uint32_t *a_dev);
+int cusmc_stratified_host(cusmc_ctx *ctx, const double *w, uint32_t N, uint64_t seed, uint32_t step, uint32_t *a);
+/* The same over LOG-weights: lw_max = largest non-NaN entry (degenerate: none, -inf or +inf), r_j =
+ * exp(lw_j - lw_max) as the log-weight chain evaluates it, q = 0 for NaN and -inf entries. */
+int cusmc_stratified_log_dev(cusmc_ctx *ctx, const double *logw_dev, uint32_t N, uint64_t seed, uint32_t step,
+                             uint32_t first, uint32_t count, uint32_t *a_dev);
+int cusmc_stratified_log_host(cusmc_ctx *ctx, const double *logw, uint32_t N, uint64_t seed, uint32_t step,
+                              uint32_t *a);
+/* Outputs sharded contiguously over `ndev` GPUs: every device receives the whole weight vector and computes
+ * outputs [first_r, first_r + count_r); the result is the single-device one bit for bit.  log_weights != 0: w
+ * holds log-weights.  cusmc_stratified_host / cusmc_stratified_log_host take this route themselves under
+ * CUSMC_DEVICES="0,1,...". */
+int cusmc_stratified_multi_host(const int *devices, int ndev, const double *w, uint32_t N, uint64_t seed,
+                                uint32_t step, int log_weights, uint32_t *a);
+
 /* ---- proposal draws ------------------------------------------------------------------------
  * propagate_K -- src/mcmc.cpp:90-160 (replaces mvn_sample_kernel_wrapper /
  * mvt_sample_kernel_wrapper, mvn_dist.hpp:29-32,48-54):
@@ -255,8 +283,8 @@ int cusmc_pf_step_dev(cusmc_dist *obs, int kind, float nu, const double *w_prev_
  * -> reweight.  Y is T x d (row t = y_t; the reference stores Y.col(t): run.rcpp.cpp:91).
  * Outputs (host, any may be NULL): X T x N x d, w T x N (densities, unnormalised, as
  * run.rcpp.cpp:110-116 returns them), a T x N (row 0 unwritten in the reference; zeros here).
- * resampler must be "metropolis", distribution "mvn" or "mvt" (mcmc.cpp:252-266); anything
- * else is CUSMC_EINVAL (the reference throws bad_function_call).
+ * resampler must be "metropolis" or "stratified" (cusmc_stratified_dev; B is then ignored), distribution "mvn" or
+ * "mvt" (mcmc.cpp:252-266); anything else is CUSMC_EINVAL (the reference throws bad_function_call).
  * The proposals' square roots of C0 and W are eigenSolver's, as MCMC() computes them (mcmc.cpp:70-71, 280);
  * with CUSMC_PROPOSAL_FACTOR=cholesky in the environment they are the lower Cholesky factors instead (same
  * law, other realisations; the triangular proposal kernels from d = 32 up). */
@@ -277,7 +305,8 @@ int cusmc_pf_run_host(cusmc_ctx *ctx, const double *Y, uint32_t N, int d, uint32
  * branches that differ between distinct devices, hipDeviceEnablePeerAccess, hipMemcpyPeerAsync and the peer
  * reads of kernels/gather.hip, are UNVERIFIED ON HARDWARE until a run on two physical GPUs is recorded;
  * tests/test_gpu_parity.py::test_multi_device_run_on_two_physical_gpus does it where two are visible).
- * cusmc_pf_run_host itself takes this route when the environment holds CUSMC_DEVICES="0,1,...". */
+ * cusmc_pf_run_host itself takes this route when the environment holds CUSMC_DEVICES="0,1,...".  Metropolis only:
+ * resampler "stratified" is CUSMC_EINVAL here, before any work (the sharded step is the fused Metropolis one). */
 int cusmc_pf_run_multi_host(const int *devices, int ndev, const double *Y, uint32_t N, int d, uint32_t T,
                             const double *m0, const double *C0, const double *F, const double *G,
                             const double *V, const double *W, float df, const char *resampler,

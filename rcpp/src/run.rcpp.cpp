@@ -45,7 +45,8 @@ static void writeOutput(const RowMatrix &Yt, const std::vector<double> &w, const
 //' @param V            [matrix]: Observation noise covariance
 //' @param W            [matrix]: State noise covariance
 //' @param df           [float]:  Degrees of freedom (for MVT)
-//' @param resampler    [string]: "metropolis"
+//' @param resampler    [string]: "metropolis" (B = 10 chain steps) or "stratified" (cost fixed in N,
+//'                     unbiased for any weights; one device only)
 //' @param distribution [string]: "mvn" or "mvt"
 //' @param p            [integer]: particle written to x_t_N<p>.csv
 //' @export
