@@ -51,6 +51,10 @@ SYMBOLS = [
     ("cusmc_stratified_log_dev", _i, [_vp, _vp, _u32, _u64, _u32, _u32, _u32, _vp]),
     ("cusmc_stratified_log_host", _i, [_vp, _vp, _u32, _u64, _u32, _vp]),
     ("cusmc_stratified_multi_host", _i, [C.POINTER(_i), _i, _vp, _u32, _u64, _u32, _i, _vp]),
+    ("cusmc_moments_dev", _i, [_vp, _vp, _i64, _i64, _i, _vp, _vp, _vp, _vp]),
+    ("cusmc_moments_log_dev", _i, [_vp, _vp, _i64, _i64, _i, _vp, _vp, _vp, _vp]),
+    ("cusmc_moments_host", _i, [_vp, _vp, _i64, _i64, _i, _vp, _vp, _vp, _vp]),
+    ("cusmc_moments_log_host", _i, [_vp, _vp, _i64, _i64, _i, _vp, _vp, _vp, _vp]),
     ("cusmc_propagate_dev", _i, [_vp, _i, _f, _vp, _vp, _u32, _i, _vp, _vp, _d, _u64, _u32, _u32,
                                  _u32, _vp]),
     ("cusmc_initialize_dev", _i, [_vp, _i, _f, _vp, _vp, _i, _d, _u64, _u32, _u32, _vp]),
@@ -64,6 +68,8 @@ SYMBOLS = [
                                _u32, _vp, _vp, _vp, _i]),
     ("cusmc_pf_run_host", _i, [_vp, _vp, _u32, _i, _u32, _vp, _vp, _vp, _vp, _vp, _vp, _f,
                                C.c_char_p, C.c_char_p, _u32, _d, _u64, _vp, _vp, _vp]),
+    ("cusmc_pf_run_summary_host", _i, [_vp, _vp, _u32, _i, _u32, _vp, _vp, _vp, _vp, _vp, _vp, _f,
+                                       C.c_char_p, C.c_char_p, _u32, _d, _u64, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     ("cusmc_pf_run_multi_host", _i, [C.POINTER(_i), _i, _vp, _u32, _i, _u32, _vp, _vp, _vp, _vp, _vp, _vp, _f,
                                      C.c_char_p, C.c_char_p, _u32, _d, _u64, _vp, _vp, _vp]),
 ]

@@ -31,7 +31,8 @@ from ._lib import MVN as _MVN, MVT as _MVT, OUT_DENSITY, OUT_LOG, CusmcError, ch
 
 __all__ = ["Context", "MultiVariateNormalDistribution", "MultiVariateTStudentDistribution",
            "Sampler", "propagate_dev", "initialize_dev", "MVN", "MVNPDF", "MVT", "MVTPDF", "metropolis_hastings", "run",
-           "set_seed", "eigenSolver", "cholesky_batched", "logpdf_percov", "CusmcError"]
+           "set_seed", "eigenSolver", "cholesky_batched", "logpdf_percov", "weighted_moments", "weighted_moments_dev",
+           "CusmcError"]
 
 SQRT3 = 1.7320508075688772  # the reference CPU transform's std-dev inflation
 
@@ -489,6 +490,59 @@ class Sampler:
         return Sampler.stratified_dev(logw, a, t=t, seed=seed, first=first, log=True, ctx=ctx)
 
 
+def _moments_input(X, w):
+    X = _f64(X)
+    if X.ndim == 1:
+        X = X.reshape(-1, 1)
+    w = _f64(w).reshape(-1)
+    if X.ndim != 2 or X.shape[0] != w.shape[0] or X.shape[0] < 1 or X.shape[1] < 1:
+        raise ValueError("X must be N x d and w of length N (N, d >= 1), got %s and %s" % (X.shape, w.shape))
+    return X, w
+
+
+def weighted_moments(X, w, log=False, cov=True, ctx=None):
+    """Weighted mean, covariance (cov=False skips it), effective sample size and log mean weight of the N rows of X
+    under weights w (densities, or log-weights with log=True): cusmc_moments_host, DESIGN.md section 4.8.
+    Returns {"mean": d, "cov": d x d or None, "ess": float, "loglik_increment": float}."""
+    X, w = _moments_input(X, w)
+    N, d = X.shape
+    ctx = ctx or default_context()
+    mean = np.empty(d)
+    P = np.empty((d, d)) if cov else None
+    stats = np.empty(2)
+    entry = _lib.lib().cusmc_moments_log_host if log else _lib.lib().cusmc_moments_host
+    check(entry(ctx._h, _ptr(X), N, d, d, _ptr(w), _ptr(mean), _ptr(P), _ptr(stats)))
+    return {"mean": mean, "cov": P, "ess": float(stats[0]), "loglik_increment": float(stats[1])}
+
+
+def weighted_moments_dev(X, w, mean, cov, stats, log=False, ctx=None):
+    """Device-resident weighted_moments, asynchronous on the context's stream: X float64 CUDA N x d with unit inner
+    stride (rows may be X.stride(0) apart), w N weights, mean d, cov d x d (or None), stats 2 (ESS, ell)."""
+    import torch
+    ctx = ctx or default_context()
+    if X.dim() != 2 or X.stride(1) != 1:
+        raise ValueError("X must be N x d with unit inner stride")
+    N, d = X.shape
+    if N < 1 or d < 1:
+        raise ValueError("X must have N, d >= 1, got %s" % (tuple(X.shape),))
+    # the same rule as the distributions' _tensor_args: a broadcast view (stride 0) or any other overlap is refused
+    ldx = X.stride(0) if N > 1 else d
+    if ldx < d:
+        raise ValueError("rows of X overlap (row stride %d < d = %d)" % (ldx, d))
+    if not (X.is_cuda and X.dtype == torch.float64):
+        raise ValueError("X must be a float64 CUDA tensor")
+    _dev_vector(w, "w", (torch.float64,), N)
+    _dev_vector(mean, "mean", (torch.float64,), d)
+    if cov is not None:
+        _dev_vector(cov, "cov", (torch.float64,), d * d)
+    _dev_vector(stats, "stats", (torch.float64,), 2)
+    entry = _lib.lib().cusmc_moments_log_dev if log else _lib.lib().cusmc_moments_dev
+    check(entry(ctx._h, C.c_void_p(X.data_ptr()), N, ldx, d, C.c_void_p(w.data_ptr()),
+                C.c_void_p(mean.data_ptr()), None if cov is None else C.c_void_p(cov.data_ptr()),
+                C.c_void_p(stats.data_ptr())))
+    return mean, cov, stats
+
+
 def propagate_dev(X_prev, a, G, Q, X_out, kind="mvn", nu=0.0, scale=1.0, seed=0, step=1, first=0, ctx=None):
     """propagate_K on device-resident tensors (src/mcmc.cpp:90-160):
     X_out[i] = [diag(c)] Q (scale xi) + G X_prev[a[i]] for the rows [first, first + len(X_out)).
@@ -642,7 +696,8 @@ def metropolis_hastings(w, N, B):
 
 
 def run(N, d, timeSteps, Y, m0, C0, F, G, V, W, df, resampler, distribution, p=0, B=10,
-        compat=False, seed=None, write_csv=False, return_ancestors=False, devices=None):
+        compat=False, seed=None, write_csv=False, return_ancestors=False, devices=None, summaries=False,
+        history=True, summary_cov=True):
     """List run(N, d, timeSteps, Y, m0, C0, F, G, V, W, df, resampler, distribution, p)
     -- src/run.rcpp.cpp:58-126.  Returns {"weights": T x N, "posterior_x": T x N x d}.
     df reaches the filter as df (the reference passes it in the wrong slot: SURVEY.md F8).
@@ -650,7 +705,19 @@ def run(N, d, timeSteps, Y, m0, C0, F, G, V, W, df, resampler, distribution, p=0
     "stratified" (Sampler.stratified; B is ignored; one device only).
     devices = [0, 1, ...] shards the particles over those GPUs below the C ABI
     (cusmc_pf_run_multi_host; same numbers as one GPU); the environment variable CUSMC_DEVICES="0,1,..."
-    does the same for callers that cannot pass the argument (the R package)."""
+    does the same for callers that cannot pass the argument (the R package).
+    summaries=True adds the filter's per-step summaries, computed on the device (cusmc_pf_run_summary_host,
+    DESIGN.md section 4.8): "mean" T x d, "cov" T x d x d, "ess" T, "loglik_increments" T (0 at t = 0) and
+    "loglik", their sum log p^(y_1:T) (unbiased in p with the stratified resampler only); summary_cov=False
+    leaves out "cov" and its T x d x d device table.  history=False keeps no history on the host or the device (no
+    "weights" / "posterior_x"): the particles take O(N d) device memory whatever T is, the summary table
+    T (d + 2) doubles, plus T d^2 with the covariance."""
+    if not history and not summaries:
+        raise ValueError("history=False needs summaries=True: the run would return nothing")
+    if not history and (write_csv or return_ancestors):
+        raise ValueError("write_csv and return_ancestors need history=True")
+    if summaries and devices is not None:
+        raise ValueError("summaries are not available in the sharded filter (devices=...)")
     N, d, T = int(N), int(d), int(timeSteps)
     if not 0 <= int(p) < N:
         raise ValueError("p = %d must satisfy 0 <= p < N" % p)  # assert(p < N): run.rcpp.cpp:64
@@ -666,12 +733,27 @@ def run(N, d, timeSteps, Y, m0, C0, F, G, V, W, df, resampler, distribution, p=0
             raise ValueError("%s must be %d x %d, got %s" % (name, d, d, m.shape))
     if m0.reshape(-1).shape[0] != d:
         raise ValueError("m0 must have %d entries" % d)
-    X = np.empty((T, N, d))
-    w = np.empty((T, N))
+    X = np.empty((T, N, d)) if history else None
+    w = np.empty((T, N)) if history else None
     a = np.empty((T, N), dtype=np.uint32) if return_ancestors else None  # (not copied back unless asked for)
     tail = (_ptr(Yt), N, d, T, _ptr(m0), _ptr(C0), _ptr(F), _ptr(G), _ptr(V), _ptr(W), C.c_float(df),
             str(resampler).encode(), str(distribution).encode(), int(B), SQRT3 if compat else 1.0, int(seed),
             _ptr(X), _ptr(w), _ptr(a))
+    if summaries:
+        sm = {"mean": np.empty((T, d)), "ess": np.empty(T), "loglik_increments": np.empty(T)}
+        if summary_cov:
+            sm["cov"] = np.empty((T, d, d))
+        check(_lib.lib().cusmc_pf_run_summary_host(default_context()._h, *tail, _ptr(sm["mean"]), _ptr(sm.get("cov")),
+                                                   _ptr(sm["ess"]), _ptr(sm["loglik_increments"])))
+        sm["loglik"] = float(sm["loglik_increments"].sum())
+        out = {"weights": w, "posterior_x": X} if history else {}
+        out.update(sm)
+        if return_ancestors:
+            out["ancestors"] = a
+        if write_csv:
+            from .io import writeOutput
+            writeOutput(Yt, w, X, N, d, T, int(p))
+        return out
     if devices is not None:
         devs = (C.c_int * len(devices))(*[int(v) for v in devices])
         check(_lib.lib().cusmc_pf_run_multi_host(devs, len(devices), *tail))

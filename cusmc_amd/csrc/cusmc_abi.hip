@@ -129,6 +129,7 @@ struct cusmc_ctx {
   StagingRing ring;  // pinned staging for small parameter uploads
   DevBuf whi;        // high words of the weight vector (resampler, large N)
   DevBuf strat;      // stratified resampler: partial maxima, tile prefixes, tile-local prefix sums
+  DevBuf moments;    // weighted moments: chunk partials (kernels/moments.hip)
   DevBuf nb4_pool;   // tail-pool counters of the assembly log-pdf kernel (kernels/logpdf_nb4_gfx950.s)
   cusmc::Nb4Pool nb4_state;
   DevBuf step_mats;  // [Q | G] of the fused filter step, re-uploaded only when they change
@@ -591,6 +592,7 @@ CUSMC_EXPORT int cusmc_ctx_destroy(cusmc_ctx *ctx)
     ctx->draw_img.release();
     ctx->whi.release();
     ctx->strat.release();
+    ctx->moments.release();
     ctx->nb4_pool.release();
     ctx->step_mats.release();
     ctx->ring.release();
@@ -1046,6 +1048,84 @@ CUSMC_EXPORT int cusmc_stratified_multi_host(const int *devices, int ndev, const
                                              uint32_t step, int log_weights, uint32_t *a)
 {
   return multi_stratified(devices, ndev, w, N, seed, step, log_weights != 0, a);
+}
+
+// ---- weighted moments ---------------------------------------------------------------
+namespace {
+
+// argument rules of the cusmc_moments_* family, checked before the context (no device needed)
+int moments_check(const void *X, int64_t N, int64_t ldx, int d, const void *w, const void *mean, const void *stats)
+{
+  if (!X || !w || !mean || !stats) return fail(CUSMC_EINVAL, "null pointer argument (X, w, mean and stats are required)");
+  if (N < 1 || d < 1 || ldx < d) return fail(CUSMC_EINVAL, "bad sizes: N = %lld, d = %d, ldx = %lld", (long long)N, d, (long long)ldx);
+  if (d > CUSMC_MAX_DIM) return fail(CUSMC_ERANGE, "d = %d exceeds CUSMC_MAX_DIM = %d", d, CUSMC_MAX_DIM);
+  return CUSMC_OK;
+}
+
+// enqueue on ctx->stream (arguments already checked)
+int moments_enqueue(cusmc_ctx *ctx, const double *X_dev, int64_t N, int64_t ldx, int d, const double *w_dev, bool logw,
+                    double *mean_dev, double *cov_dev, double *stats_dev)
+{
+  if (int rc = ctx->moments.reserve(cusmc::moments_workspace_bytes(N, d, cov_dev != nullptr))) return rc;
+  HIP_TRY(cusmc::launch_moments(X_dev, N, ldx, d, w_dev, logw, mean_dev, cov_dev, stats_dev, ctx->moments.p,
+                                ctx->stream));
+  return CUSMC_OK;
+}
+
+int moments_dev(cusmc_ctx *ctx, const double *X_dev, int64_t N, int64_t ldx, int d, const double *w_dev, bool logw,
+                double *mean_dev, double *cov_dev, double *stats_dev)
+{
+  if (int rc = moments_check(X_dev, N, ldx, d, w_dev, mean_dev, stats_dev)) return rc;
+  if (int rc = activate(ctx)) return rc;
+  return moments_enqueue(ctx, X_dev, N, ldx, d, w_dev, logw, mean_dev, cov_dev, stats_dev);
+}
+
+int moments_host(cusmc_ctx *ctx, const double *X, int64_t N, int64_t ldx, int d, const double *w, bool logw,
+                 double *mean, double *cov, double *stats)
+{
+  if (int rc = moments_check(X, N, ldx, d, w, mean, stats)) return rc;
+  if (int rc = activate(ctx)) return rc;
+  const size_t xbytes = ((size_t)(N - 1) * ldx + d) * 8;
+  const size_t obytes = ((size_t)d + (cov ? (size_t)d * d : 0) + 2) * 8;
+  if (int rc = ctx->scratch[0].reserve(xbytes)) return rc;
+  if (int rc = ctx->scratch[2].reserve((size_t)N * 8)) return rc;
+  if (int rc = ctx->scratch[1].reserve(obytes)) return rc;
+  double *Xd = (double *)ctx->scratch[0].p, *wd = (double *)ctx->scratch[2].p, *od = (double *)ctx->scratch[1].p;
+  HIP_TRY(hipMemcpyAsync(Xd, X, xbytes, hipMemcpyHostToDevice, ctx->stream));
+  HIP_TRY(hipMemcpyAsync(wd, w, (size_t)N * 8, hipMemcpyHostToDevice, ctx->stream));
+  double *md = od, *sd = od + d, *cd = cov ? od + d + 2 : nullptr;
+  if (int rc = moments_enqueue(ctx, Xd, N, ldx, d, wd, logw, md, cd, sd)) return rc;
+  HIP_TRY(hipMemcpyAsync(mean, md, (size_t)d * 8, hipMemcpyDeviceToHost, ctx->stream));
+  HIP_TRY(hipMemcpyAsync(stats, sd, 16, hipMemcpyDeviceToHost, ctx->stream));
+  if (cov) HIP_TRY(hipMemcpyAsync(cov, cd, (size_t)d * d * 8, hipMemcpyDeviceToHost, ctx->stream));
+  HIP_TRY(hipStreamSynchronize(ctx->stream));
+  return CUSMC_OK;
+}
+
+}  // namespace
+
+CUSMC_EXPORT int cusmc_moments_dev(cusmc_ctx *ctx, const double *X_dev, int64_t N, int64_t ldx, int d,
+                                   const double *w_dev, double *mean_dev, double *cov_dev, double *stats_dev)
+{
+  return moments_dev(ctx, X_dev, N, ldx, d, w_dev, false, mean_dev, cov_dev, stats_dev);
+}
+
+CUSMC_EXPORT int cusmc_moments_log_dev(cusmc_ctx *ctx, const double *X_dev, int64_t N, int64_t ldx, int d,
+                                       const double *logw_dev, double *mean_dev, double *cov_dev, double *stats_dev)
+{
+  return moments_dev(ctx, X_dev, N, ldx, d, logw_dev, true, mean_dev, cov_dev, stats_dev);
+}
+
+CUSMC_EXPORT int cusmc_moments_host(cusmc_ctx *ctx, const double *X, int64_t N, int64_t ldx, int d, const double *w,
+                                    double *mean, double *cov, double *stats)
+{
+  return moments_host(ctx, X, N, ldx, d, w, false, mean, cov, stats);
+}
+
+CUSMC_EXPORT int cusmc_moments_log_host(cusmc_ctx *ctx, const double *X, int64_t N, int64_t ldx, int d,
+                                        const double *logw, double *mean, double *cov, double *stats)
+{
+  return moments_host(ctx, X, N, ldx, d, logw, true, mean, cov, stats);
 }
 
 // ---- proposal draws -------------------------------------------------------------------------
@@ -1552,11 +1632,15 @@ int pf_obs_table(cusmc_dist *obs, bool fused, const double *G, const double *Qw,
   return CUSMC_OK;
 }
 
-// the whole filter on ONE device (the environment is not consulted here)
+// the whole filter on ONE device (the environment is not consulted here).  A history array is kept whole on the
+// device only when its output is wanted; otherwise X and w live in a ring of two steps (slot t & 1) and a in one.
+// Any non-NULL summary output adds the moments of (X_t, w_t) after every step t into a T-row device table
+// (kernels/moments.hip), copied out once at the end; ell_0 = 0 by definition.
 int pf_run_single(cusmc_ctx *ctx, const double *Y, uint32_t N, int d, uint32_t T, const double *m0, const double *C0,
                   const double *F, const double *G, const double *V, const double *W, float df, const char *resampler,
                   const char *distribution, uint32_t B, double scale, uint64_t seed, double *X_out, double *w_out,
-                  uint32_t *a_out)
+                  uint32_t *a_out, double *mean_out = nullptr, double *cov_out = nullptr, double *ess_out = nullptr,
+                  double *loglik_out = nullptr)
 {
   if (int rc = activate(ctx)) return rc;
   // validate the option strings BEFORE any work: the reference default-constructs an empty
@@ -1605,14 +1689,19 @@ int pf_run_single(cusmc_ctx *ctx, const double *Y, uint32_t N, int d, uint32_t T
   const uint32_t nchunks = (T + chunk_steps - 1) / chunk_steps;
   std::vector<hipEvent_t> chunk_done(nchunks, nullptr);
   hipStream_t copy_stream = nullptr;
-  int rc = dX.reserve(slice * T * 8);
-  if (!rc) rc = dw.reserve((size_t)N * T * 8);
-  if (!rc) rc = da.reserve((size_t)N * T * 4);
+  const size_t xsteps = X_out ? T : std::min<uint32_t>(T, 2), wsteps = w_out ? T : std::min<uint32_t>(T, 2);
+  const bool summaries = mean_out || cov_out || ess_out || loglik_out;
+  DevBuf dsum;  // summary table: mean T x d, stats T x 2 (ESS, ell), cov T x d x d
+  const size_t sum_doubles = (size_t)T * d + (size_t)T * 2 + (cov_out ? (size_t)T * d * d : 0);
+  int rc = dX.reserve(slice * xsteps * 8);
+  if (!rc) rc = dw.reserve((size_t)N * wsteps * 8);
+  if (!rc) rc = da.reserve((size_t)N * (a_out ? T : 1) * 4);
+  if (!rc && summaries) rc = dsum.reserve(sum_doubles * 8);
   auto cleanup = [&](int code) {
     (void)hipStreamSynchronize(ctx->stream);
     if (copy_stream) { (void)hipStreamSynchronize(copy_stream); (void)hipStreamDestroy(copy_stream); }
     for (hipEvent_t ev : chunk_done) if (ev) (void)hipEventDestroy(ev);
-    dX.release(); dw.release(); da.release(); whi2.release(); ytab.dev.release();
+    dX.release(); dw.release(); da.release(); whi2.release(); ytab.dev.release(); dsum.release();
     cusmc_dist_destroy(obs);
     return code;
   };
@@ -1628,6 +1717,15 @@ int pf_run_single(cusmc_ctx *ctx, const double *Y, uint32_t N, int d, uint32_t T
   phase("device allocation");
   double *X = (double *)dX.p, *w = (double *)dw.p;
   uint32_t *a = (uint32_t *)da.p;
+  auto X_at = [&](uint32_t t) { return X + (size_t)(X_out ? t : t & 1) * slice; };
+  auto w_at = [&](uint32_t t) { return w + (size_t)(w_out ? t : t & 1) * N; };
+  auto a_at = [&](uint32_t t) { return a + (size_t)(a_out ? t : 0) * N; };
+  double *sum_mean = (double *)dsum.p, *sum_stats = sum_mean + (size_t)T * d, *sum_cov = sum_stats + (size_t)T * 2;
+  auto summary = [&](uint32_t t) -> int {
+    if (!summaries) return CUSMC_OK;
+    return moments_enqueue(ctx, X_at(t), N, d, d, w_at(t), false, sum_mean + (size_t)t * d,
+                           cov_out ? sum_cov + (size_t)t * d * d : nullptr, sum_stats + (size_t)t * 2);
+  };
 
   // initialize(): x_0 ~ dist(m0).sample(Q0); w_0 = 1/N        src/mcmc.cpp:76-85
   rc = cusmc_initialize_dev(ctx, kind, df, m0, Q0.data(), d, scale, seed, 0, N, X);
@@ -1639,7 +1737,8 @@ int pf_run_single(cusmc_ctx *ctx, const double *Y, uint32_t N, int d, uint32_t T
         hipStreamSynchronize(ctx->stream) != hipSuccess)
       return cleanup(fail(CUSMC_EHIP, "initial weight upload failed"));
   }
-  rc = mark(0);
+  rc = summary(0);
+  if (!rc) rc = mark(0);
   if (rc) return cleanup(rc);
   // MCMC(): for t = 1..T-1: resample -> propagate -> reweight   src/mcmc.cpp:292-308
   if (T > 1) {
@@ -1658,9 +1757,9 @@ int pf_run_single(cusmc_ctx *ctx, const double *Y, uint32_t N, int d, uint32_t T
         return cleanup(fail(CUSMC_EHIP, "%s building the weight table", hipGetErrorString(e)));
     }
     for (uint32_t t = 1; t < T; ++t) {
-      const double *w_prev = w + (size_t)(t - 1) * N, *X_prev = X + (size_t)(t - 1) * slice;
-      uint32_t *a_t = a + (size_t)t * N;
-      double *X_t = X + (size_t)t * slice, *w_t = w + (size_t)t * N;
+      const double *w_prev = w_at(t - 1), *X_prev = X_at(t - 1);
+      uint32_t *a_t = a_at(t);
+      double *X_t = X_at(t), *w_t = w_at(t);
       const double *shift_t = ytab.shift(obs, t), *bias_t = ytab.bias(obs, t);
       if (carry_hi) {
         cusmc::ShardStep st;
@@ -1687,6 +1786,7 @@ int pf_run_single(cusmc_ctx *ctx, const double *Y, uint32_t N, int d, uint32_t T
         if (!rc) rc = draws(ctx, kind, df, X_prev, a_t, G, Qw.data(), nullptr, d, scale, seed, t, 2u, 0, N, X_t);
         if (!rc) rc = run_logpdf(obs, X_t, N, d, CUSMC_OUT_DENSITY, w_t, shift_t, bias_t);
       }
+      if (!rc) rc = summary(t);
       if (!rc) rc = mark(t);
       if (rc) return cleanup(rc);
     }
@@ -1750,6 +1850,18 @@ int pf_run_single(cusmc_ctx *ctx, const double *Y, uint32_t N, int d, uint32_t T
     if (e != hipSuccess) return cleanup(fail(CUSMC_EHIP, "%s copying filter outputs", hipGetErrorString(e)));
   }
   phase("page faults + device-to-host copies (overlapping the loop)");
+  if (summaries) {
+    std::vector<double> host(sum_doubles);
+    if (hipMemcpy(host.data(), dsum.p, sum_doubles * 8, hipMemcpyDeviceToHost) != hipSuccess)
+      return cleanup(fail(CUSMC_EHIP, "copying filter summaries failed"));
+    const double *hs = host.data() + (size_t)T * d;
+    if (mean_out) std::copy(host.data(), host.data() + (size_t)T * d, mean_out);
+    if (cov_out) std::copy(hs + (size_t)T * 2, hs + (size_t)T * 2 + (size_t)T * d * d, cov_out);
+    for (uint32_t t = 0; t < T; ++t) {
+      if (ess_out) ess_out[t] = hs[2 * t];
+      if (loglik_out) loglik_out[t] = t == 0 ? 0.0 : hs[2 * t + 1];  // (ell_0 = 0: y_0 is not used)
+    }
+  }
   const int done = cleanup(CUSMC_OK);
   phase("device memory released");
   return done;
@@ -1775,6 +1887,28 @@ CUSMC_EXPORT int cusmc_pf_run_host(cusmc_ctx *ctx, const double *Y, uint32_t N, 
                                    distribution, B, scale, seed, X_out, w_out, a_out);
   return pf_run_single(ctx, Y, N, d, T, m0, C0, F, G, V, W, df, resampler, distribution, B, scale, seed, X_out, w_out,
                        a_out);
+}
+
+CUSMC_EXPORT int cusmc_pf_run_summary_host(cusmc_ctx *ctx, const double *Y, uint32_t N, int d, uint32_t T,
+                                           const double *m0, const double *C0, const double *F, const double *G,
+                                           const double *V, const double *W, float df, const char *resampler,
+                                           const char *distribution, uint32_t B, double scale, uint64_t seed,
+                                           double *X_out, double *w_out, uint32_t *a_out, double *mean_out,
+                                           double *cov_out, double *ess_out, double *loglik_out)
+{
+  const bool summaries = mean_out || cov_out || ess_out || loglik_out;
+  std::vector<int> devs;
+  if (int rc = env_devices(devs)) return rc;
+  if (summaries && !devs.empty())
+    return fail(CUSMC_EINVAL, "filter summaries are not available in the sharded filter (CUSMC_DEVICES is set); "
+                "unset it or pass NULL summary outputs");
+  if (int rc = activate(ctx)) return rc;
+  if (!devs.empty() && !(devs.size() == 1 && devs[0] == ctx->device))
+    return cusmc_pf_run_multi_host(devs.data(), (int)devs.size(), Y, N, d, T, m0, C0, F, G, V, W, df, resampler,
+                                   distribution, B, scale, seed, X_out, w_out, a_out);
+  if (summaries && d > CUSMC_MAX_DIM) return fail(CUSMC_ERANGE, "d = %d exceeds CUSMC_MAX_DIM = %d", d, CUSMC_MAX_DIM);
+  return pf_run_single(ctx, Y, N, d, T, m0, C0, F, G, V, W, df, resampler, distribution, B, scale, seed, X_out, w_out,
+                       a_out, mean_out, cov_out, ess_out, loglik_out);
 }
 
 // ---- the filter on several GPUs ---------------------------------------------------------------------

@@ -115,6 +115,13 @@ hipError_t launch_metropolis(const double *w, const uint32_t *whi, uint32_t N, u
                              uint32_t step, uint32_t first, uint32_t count, uint32_t *a, int num_cus,
                              hipStream_t stream);
 
+// --- kernels/moments.hip ---------------------------------------------------------------------------------------
+// weighted mean, covariance (cov may be null), stats = [ESS, ell] of N rows of X (ldx apart) under weights w
+// (log_weights: log-weights); workspace: device memory of moments_workspace_bytes(N, d, cov != null)
+size_t moments_workspace_bytes(int64_t N, int d, bool with_cov);
+hipError_t launch_moments(const double *X, int64_t N, int64_t ldx, int d, const double *w, bool log_weights,
+                          double *mean, double *cov, double *stats, void *workspace, hipStream_t stream);
+
 // --- kernels/resample_stratified.hip ------------------------------------------------------------
 // stratified ancestors of outputs [first, first + count) over all N (log-)weights; workspace: device memory of
 // stratified_workspace_bytes(N) (no initialisation needed)

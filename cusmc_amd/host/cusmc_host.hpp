@@ -9,6 +9,7 @@
 //   Sampler::metropolis_hastings              inst/include/samplers.hpp:7-18, src/samplers.cpp:7-36
 //   Sampler::stratified                       (no reference counterpart: DESIGN.md section 4.7)
 //   particle_filter                           inst/include/particle_filter.hpp:12-19
+//   particle_filter_summary, weighted_moments (no reference counterpart: DESIGN.md section 4.8)
 // Errors: the reference dies through Rcpp::stop (inst/include/support.cuh:9-14); here every
 // non-zero ABI status throws cusmc::Error carrying cusmc_last_error().
 #ifndef CUSMC_HOST_HPP
@@ -193,6 +194,36 @@ inline void particle_filter(double *post_x_t, double *w_t, unsigned *a_t, const 
                           F.row_major().data(), G.row_major().data(), sigmaV.row_major().data(),
                           sigmaW.row_major().data(), df, resampler_opt.c_str(), distribution_opt.c_str(), B, 1.0,
                           seed, post_x_t, w_t, a_t));
+}
+
+// particle_filter() plus per-step summaries (cusmc_pf_run_summary_host): any output may be nullptr.  The
+// history-free form (post_x_t, w_t, a_t all nullptr) keeps the particles in O(N d) device memory whatever
+// timeSteps is; the summary table takes T (d + 2) doubles, plus T d^2 with cov_t.
+// mean_t T x d, cov_t T x d x d, ess_t T, loglik_t T (loglik_t[0] = 0; the sum is log p^(y_1:T)).
+inline void particle_filter_summary(double *post_x_t, double *w_t, unsigned *a_t, double *mean_t, double *cov_t,
+                                    double *ess_t, double *loglik_t, const double *y_t, const Matrix &F,
+                                    const Matrix &G, const Vector &m0, const Matrix &C0, const Matrix &sigmaV,
+                                    const Matrix &sigmaW, dim_t N, dim_t d, dim_t timeSteps, float df,
+                                    const std::string &resampler_opt, const std::string &distribution_opt,
+                                    uint64_t seed = 0, unsigned B = 10)
+{
+  check(cusmc_pf_run_summary_host(Context::instance().get(), y_t, N, (int)d, timeSteps, m0.data(),
+                                  C0.row_major().data(), F.row_major().data(), G.row_major().data(),
+                                  sigmaV.row_major().data(), sigmaW.row_major().data(), df, resampler_opt.c_str(),
+                                  distribution_opt.c_str(), B, 1.0, seed, post_x_t, w_t, a_t, mean_t, cov_t, ess_t,
+                                  loglik_t));
+}
+
+// Weighted mean, covariance (cov may be nullptr), ESS and log mean weight of N particles (X N x d row-major) under
+// weights w (log_weights: log-weights); cusmc_moments_host, DESIGN.md section 4.8.
+inline void weighted_moments(const double *X, size_t N, dim_t d, const double *w, double *mean, double *cov,
+                             double *ess, double *loglik_increment, bool log_weights = false)
+{
+  double stats[2];
+  check((log_weights ? cusmc_moments_log_host : cusmc_moments_host)(Context::instance().get(), X, (int64_t)N,
+                                                                     (int64_t)d, (int)d, w, mean, cov, stats));
+  if (ess) *ess = stats[0];
+  if (loglik_increment) *loglik_increment = stats[1];
 }
 
 // The same filter with the particles sharded over several GPUs of the node (cusmc_pf_run_multi_host: one host

@@ -203,6 +203,30 @@ int cusmc_stratified_log_host(cusmc_ctx *ctx, const double *logw, uint32_t N, ui
 int cusmc_stratified_multi_host(const int *devices, int ndev, const double *w, uint32_t N, uint64_t seed,
                                 uint32_t step, int log_weights, uint32_t *a);
 
+/* ---- weighted moments -------------------------------------------------------------
+ * The summaries a particle filter is read by, of N particles x_i (rows of X, ldx doubles apart, d components) and
+ * their weights:
+ *     densities w:     M = largest w_i > 0 (NaN excluded); w^_i = w_i / M for w_i > 0, else 0 (zero, negative and
+ *                      NaN weights count as 0, as in both resamplers)
+ *     log-weights lw:  M = largest non-NaN lw_i; w^_i = exp(lw_i - M) as the log-weight resamplers evaluate it
+ *                      (NaN and -inf give 0)
+ *     W = sum w^_i;  mean m = sum w^_i x_i / W;  cov P = sum w^_i (x_i - m)(x_i - m)^T / W (no bias correction;
+ *     d x d row-major, both triangles bitwise equal);  stats[0] = ESS = W^2 / sum w^_i^2;
+ *     stats[1] = ell = log(W / N) + log M (log-weights: + M), the log of the mean weight.
+ * No positive weight: m, P NaN, ESS 0, ell -inf.  M = +inf: m, P, ESS NaN, ell +inf.  Two passes (P is the
+ * centred moment about the computed m); the reduction order is fixed by a chunk partition that depends on
+ * (N, d) alone, so results are bitwise reproducible and equal across entry points and streams.
+ * cov may be NULL (the second pass is skipped).  N < 1, d < 1, ldx < d and NULL X, w, mean or stats are
+ * CUSMC_EINVAL; d > CUSMC_MAX_DIM is CUSMC_ERANGE.  The _dev forms are asynchronous on the context's stream. */
+int cusmc_moments_dev(cusmc_ctx *ctx, const double *X_dev, int64_t N, int64_t ldx, int d, const double *w_dev,
+                      double *mean_dev, double *cov_dev, double *stats_dev);
+int cusmc_moments_log_dev(cusmc_ctx *ctx, const double *X_dev, int64_t N, int64_t ldx, int d,
+                          const double *logw_dev, double *mean_dev, double *cov_dev, double *stats_dev);
+int cusmc_moments_host(cusmc_ctx *ctx, const double *X, int64_t N, int64_t ldx, int d, const double *w,
+                       double *mean, double *cov, double *stats);
+int cusmc_moments_log_host(cusmc_ctx *ctx, const double *X, int64_t N, int64_t ldx, int d, const double *logw,
+                           double *mean, double *cov, double *stats);
+
 /* ---- proposal draws ------------------------------------------------------------------------
  * propagate_K -- src/mcmc.cpp:90-160 (replaces mvn_sample_kernel_wrapper /
  * mvt_sample_kernel_wrapper, mvn_dist.hpp:29-32,48-54):
@@ -293,6 +317,23 @@ int cusmc_pf_run_host(cusmc_ctx *ctx, const double *Y, uint32_t N, int d, uint32
                       const double *V, const double *W, float df, const char *resampler,
                       const char *distribution, uint32_t B, double scale, uint64_t seed,
                       double *X_out, double *w_out, uint32_t *a_out);
+
+/* cusmc_pf_run_host plus per-step summaries; every output may be NULL.  Row t of mean_out (T x d), cov_out
+ * (T x d x d), ess_out (T) and loglik_out (T) is the moments of (X_t, w_t) as cusmc_moments_dev computes them,
+ * bitwise.  loglik_out[t] = log((1/N) sum_i w_t^i) for t >= 1, the bootstrap filter's increment, so that
+ * sum_t loglik_out[t] = log p^(y_1:T); loglik_out[0] = 0 (w_0 = 1/N, y_0 unused).  The estimate is unbiased in p
+ * only with the stratified resampler: the Metropolis chain with finite B is itself biased.
+ * History arrays whose output is NULL are not kept on the device (X and w in a ring of two steps, a in one):
+ * with X_out, w_out and a_out all NULL the particles take O(N d) device memory, independent of T; the summary
+ * table stays on the device until the end: T (d + 2) doubles, plus T d^2 when cov_out is non-NULL.  The histories returned
+ * are cusmc_pf_run_host's bitwise.  Summaries are single-device: with CUSMC_DEVICES set, any non-NULL summary
+ * output is CUSMC_EINVAL before any work. */
+int cusmc_pf_run_summary_host(cusmc_ctx *ctx, const double *Y, uint32_t N, int d, uint32_t T,
+                              const double *m0, const double *C0, const double *F, const double *G,
+                              const double *V, const double *W, float df, const char *resampler,
+                              const char *distribution, uint32_t B, double scale, uint64_t seed,
+                              double *X_out, double *w_out, uint32_t *a_out, double *mean_out, double *cov_out,
+                              double *ess_out, double *loglik_out);
 
 /* The same filter with the particles sharded over `ndev` GPUs of one node (contiguous shards, one host
  * thread + library-owned context per shard, peer access over xGMI) -- the loop of src/mcmc.cpp:292-308 being
